@@ -13,6 +13,18 @@ Scaling (cocoa_amd.configs): weak by default -- every GPU holds its own
 globally, H unchanged); --scaling strong keeps one fixed problem (n, K) and
 splits its partitions over the GPUs (C3: K = 64 on 1-8 GPUs; C4: K = 1,024).
 
+A plain run sets up, warms up, times --steps steps, writes its outputs when
+--dump-outputs DIR is given and prints the result line: nothing else.  --full
+adds what takes work of its own: HIP events around the solver (kernel_ms, the
+rooflines), the evaluation alone, the GPU's clocks / power / temperature
+(amdsmi), a fresh run to the duality-gap target and the CPU baseline.
+
+--dump-outputs DIR writes what the last timed step left with its caller, as
+float64 .npy files: w (the model, d), alpha (rank 0's dual variables, n),
+eval (that step's evaluation, the fields of EVAL_FIELDS in order) and
+gap_trajectory (the value every timed step read back).  The problem is seeded
+(cocoa_amd.configs), so the same arguments give the same inputs every run.
+
 Prints one JSON line (rank 0).  N > 1 ranks, one process per GPU, either way:
   python bench.py --gpus N      (this process spawns the N ranks itself, before
                                  any GPU call, and relays rank 0's line)
@@ -35,9 +47,24 @@ sys.path.insert(0, ROOT)
 
 METRIC = "CoCoA+ SVM wall-clock to duality gap 1e-4; coord updates/s at 1/2/4/8 GPUs"
 PEAK_HBM_GBS = 8000.0  # MI355X_MICROARCH.md: HBM3E 8.0 TB/s peak
+# eval.npy of --dump-outputs: cocoa_eval's result (include/cocoa_capi.h), in this order
+EVAL_FIELDS = ("primal", "dual", "gap", "test_error", "hinge_sum", "alpha_sum", "w_sqnorm", "test_err_count",
+               "test_rows")
 
 
 from cocoa_amd.configs import CONFIGS  # noqa: E402  (BASELINE.json configs)
+
+
+DUMP_MAX_ELEMS = 3_500_000  # per array: w and alpha together stay under 56 MB of the 64 MB a dump may take
+
+
+def dump_sample(x):
+    """x itself up to DUMP_MAX_ELEMS elements (every BASELINE.json config), else
+    a fixed seeded sample of it in index order: the same elements every run."""
+    if x.size <= DUMP_MAX_ELEMS:
+        return x
+    idx = np.sort(np.random.default_rng(0).choice(x.size, DUMP_MAX_ELEMS, replace=False))
+    return x[idx]
 
 
 def log(*a):
@@ -276,6 +303,13 @@ def main():
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--strict", action="store_true", help="bit-exact mode (default: fast)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: per-kernel HIP events and the "
+                         "rooflines, the evaluation alone, amdsmi telemetry, the run to the gap target and the CPU "
+                         "baseline (--no-gap, --no-cpu-baseline, --stats-* and --cpu-seconds act only with --full)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed to DIR/{w,alpha,eval,"
+                         "gap_trajectory}.npy (float64; rank 0)")
     ap.add_argument("--n", type=int, default=None)
     ap.add_argument("--d", type=int, default=None)
     ap.add_argument("--nnz", type=float, default=None)
@@ -392,11 +426,16 @@ def main():
         the evaluation still ran, they took the CUs the next solver's workgroups
         need whole, 3.40 ms per step in r04f.)"""
         vals, rounds, pending = [], [], None
+
+        def got(ev):
+            last_eval[0] = ev  # (--dump-outputs: the evaluation the last step handed back)
+            vals.append(ev[key])
+
         for _ in range(count):
             runner.round(t)
             if pipe:
                 if pending is not None:
-                    vals.append(eng.eval_wait()[key])
+                    got(eng.eval_wait())
                     rounds.append(pending)
                     if stop and stop(vals[-1]):  # (round t is still running; nothing pending)
                         return vals, rounds, t + 1
@@ -404,7 +443,7 @@ def main():
                 pending = t
             elif defer:
                 if pending is not None:
-                    vals.append(runner.eval_end()[key])
+                    got(runner.eval_end())
                     rounds.append(pending)
                     pending = None
                     if stop and stop(vals[-1]):  # (round t is queued behind it; not evaluated)
@@ -412,39 +451,97 @@ def main():
                 runner.eval_begin()
                 pending = t
             else:
-                vals.append(runner.eval()[key])
+                got(runner.eval())
                 rounds.append(t)
                 if stop and stop(vals[-1]):
                     return vals, rounds, t + 1
             t += 1
         if pending is not None:
-            vals.append(eng.eval_wait()[key] if pipe else runner.eval_end()[key])
+            got(eng.eval_wait() if pipe else runner.eval_end())
             rounds.append(pending)
         return vals, rounds, t
 
-    props = torch.cuda.get_device_properties(local_rank % ndev) if torch.cuda.is_available() else None
-    tele = GpuTelemetry(getattr(props, "pci_bus_id", None), getattr(props, "pci_domain_id", None))
-    tele_before = tele.snap()
+    last_eval = [None]
+    full = args.full
+    if full:
+        props = torch.cuda.get_device_properties(local_rank % ndev) if torch.cuda.is_available() else None
+        tele = GpuTelemetry(getattr(props, "pci_bus_id", None), getattr(props, "pci_domain_id", None))
+        tele_before = tele.snap()
 
     t = 1
     _, _, t = steps(t, args.warmup)
-    eng.stats_reset()
-    # events only around the kernel the roofline reads (--stats-kernels): every
-    # bracketed launch adds two event packets and ~4-5 us of launch latency each;
-    # the evaluation's own roofline then reads the 5 launches after the timed region
-    if not args.stats_all and hasattr(cocoa_amd._capi.lib(), "cocoa_stats_kernels"):
-        eng.stats_kernels(args.stats_kernels.split(","))
-    eng.stats_enable(True)
+    if full:
+        eng.stats_reset()
+        # events only around the kernel the roofline reads (--stats-kernels): every
+        # bracketed launch adds two event packets and ~4-5 us of launch latency each;
+        # the evaluation's own roofline then reads the 5 launches after the timed region
+        if not args.stats_all and hasattr(cocoa_amd._capi.lib(), "cocoa_stats_kernels"):
+            eng.stats_kernels(args.stats_kernels.split(","))
+        eng.stats_enable(True)
     barrier()
-    tele_start = tele.snap()
-    tele.start()
+    if full:
+        tele_start = tele.snap()
+        tele.start()
     ts = time.perf_counter()
     gaps, timed_rounds, t = steps(t, args.steps)
     barrier()
     dt = max_over_ranks(time.perf_counter() - ts)
-    tele_timed = tele.stop()
-    tele_end = tele.snap()
-    stats = eng.kernel_stats()
+    updates = K_glob * H * args.steps
+    value = updates / dt
+    if full:
+        tele_timed = tele.stop()
+        tele_end = tele.snap()
+        stats = eng.kernel_stats()
+    log(f"timed {args.steps} rounds in {dt:.3f}s -> {value:.4g} updates/s" + (f"; kernels {stats}" if full else ""))
+
+    # ---- --dump-outputs: what the last timed step left with its caller -----
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        arrays = {"w": dump_sample(eng.w()), "alpha": dump_sample(eng.alpha()),
+                  "eval": np.array([last_eval[0][k] for k in EVAL_FIELDS], np.float64),
+                  "gap_trajectory": np.array(gaps, np.float64)}
+        for name, a in arrays.items():
+            np.save(os.path.join(args.dump_outputs, name + ".npy"), a)
+        dumped = {"dir": args.dump_outputs, "arrays": {k: list(a.shape) for k, a in arrays.items()},
+                  "eval_fields": list(EVAL_FIELDS), "bytes": int(sum(a.nbytes for a in arrays.values()))}
+        log(f"dumped {dumped}")
+
+    plan = eng.plan()
+    if rank == 0:
+        headline = {
+            "metric": METRIC, "value": value, "unit": "coord updates/s", "n_gpus": world, "steps": args.steps,
+            "warmup": args.warmup, "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True,
+            "scaling": args.scaling,
+            # BASELINE.md publishes no number for this metric: vs_baseline stays null
+            # (--full reports the ratio to the CPU baseline measured here on its own)
+            "vs_baseline": None,
+            "dtype": "f64",
+            "data": cfg["data"],
+            "config": {"workload": f"{args.config.upper()} {cfg['shape']} {args.method} (n={tr.n}/GPU of {n_glob}, d={args.d}, "
+                                   f"~{args.nnz} nnz/row, lambda={args.lam}, K={K_glob} ({tr.num_parts}/GPU), H=n/K={H}), "
+                                   f"step = round + {'gap' if sdca else 'primal'} eval",
+                       "method": args.method,
+                       "n_total": n_glob, "K_total": K_glob, "H": H, "nnz_per_gpu": tr.nnz, "test_rows_per_gpu": te.n,
+                       "mode": "strict" if args.strict else "fast",
+                       "eval_flow": "pipelined (cocoa_eval_async)" if pipe else
+                                    "deferred read-back (cocoa_eval_begin/_end)" if defer else "synchronous (cocoa_eval)",
+                       "parallelism": f"dp{world}: {tr.num_parts} partitions per GPU, deltaW "
+                                      f"{'all-reduce' if not args.strict else 'ordered chain'} inside libcocoa_hip.so "
+                                      f"({args.transport.upper()})"},
+            "gap_trajectory_timed": gaps,
+            "plan": plan,
+            "comm": {"transport": comm["transport"] if world > 1 else None, "world": comm["world"] if world > 1 else 1},
+            "full": full, "dump_outputs": dumped,
+        }
+    if not full:  # a plain run ends here; everything below is --full
+        if rank == 0:
+            print(json.dumps(headline), flush=True)
+        if world > 1:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
+
     # the eval pass alone (in the timed loop it overlaps the next round's solver)
     eng.stats_reset()
     if not args.stats_all and hasattr(cocoa_amd._capi.lib(), "cocoa_stats_kernels"):
@@ -454,9 +551,6 @@ def main():
         runner.eval()
     eval_alone = eng.kernel_stats().get("eval", {})
     eng.stats_enable(False)
-    updates = K_glob * H * args.steps
-    value = updates / dt
-    log(f"timed {args.steps} rounds in {dt:.3f}s -> {value:.4g} updates/s; kernels {stats}")
 
     # ---- wall-clock to duality gap <= target (fresh run) -------------------
     ttg = None
@@ -575,34 +669,16 @@ def main():
 
     if rank == 0:
         out = {
-            "metric": METRIC, "value": value, "unit": "coord updates/s", "n_gpus": world, "steps": args.steps,
-            "warmup": args.warmup, "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True,
-            "scaling": args.scaling,
-            # BASELINE.md publishes no number; its CPU-baseline plan
-            # makes the measured local[N] oracle the baseline: coord updates/s ratio
-            # BASELINE.md publishes no number for this metric: vs_baseline stays null;
+            **headline,
+            # vs_baseline stays null (BASELINE.md publishes no number for this metric);
             # the ratio to the CPU baseline measured here is reported on its own
-            "vs_baseline": None,
             "vs_cpu_baseline": (value / cpu["value"]) if cpu else None,
             "time_to_gap_vs_cpu": (cpu["time_to_gap_s"] / ttg) if (cpu and ttg and cpu.get("time_to_gap_s")) else None,
             "time_to_gap_vs_cpu16": (cpu["fair_share_16"]["time_to_gap_s"] / ttg)
             if (cpu and ttg and cpu.get("fair_share_16") and cpu["fair_share_16"].get("time_to_gap_s")) else None,
-            "dtype": "f64",
-            "data": cfg["data"],
-            "config": {"workload": f"{args.config.upper()} {cfg['shape']} {args.method} (n={tr.n}/GPU of {n_glob}, d={args.d}, "
-                                   f"~{args.nnz} nnz/row, lambda={args.lam}, K={K_glob} ({tr.num_parts}/GPU), H=n/K={H}), "
-                                   f"step = round + {'gap' if sdca else 'primal'} eval",
-                       "method": args.method,
-                       "n_total": n_glob, "K_total": K_glob, "H": H, "nnz_per_gpu": tr.nnz, "test_rows_per_gpu": te.n,
-                       "mode": "strict" if args.strict else "fast",
-                       "eval_flow": "pipelined (cocoa_eval_async)" if pipe else
-                                    "deferred read-back (cocoa_eval_begin/_end)" if defer else "synchronous (cocoa_eval)",
-                       "parallelism": f"dp{world}: {tr.num_parts} partitions per GPU, deltaW "
-                                      f"{'all-reduce' if not args.strict else 'ordered chain'} inside libcocoa_hip.so "
-                                      f"({args.transport.upper()})"},
             "time_to_gap_s": ttg, "rounds_to_gap": rounds_to_gap, "gap_target": args.gap_target,
             "gap_run_s": gap_run_s, "gap_max_rounds": args.gap_max_rounds,
-            "final_gap": final_gap, "gap_trajectory_timed": gaps,
+            "final_gap": final_gap,
             "roofline": {"kernel": "solver (local SDCA, CoCoA.localSDCA)", "bound": "hbm", "achieved": ach,
                          "peak": PEAK_HBM_GBS, "unit": "GB/s", "frac": ach / PEAK_HBM_GBS, "traffic": traffic,
                          "bytes_per_launch": b_solver, "avg_launch_ms": solver_ms,

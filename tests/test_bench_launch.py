@@ -85,3 +85,17 @@ def test_launch_probe_reports_transport():
     assert p.returncode == 0, p.stderr[-2000:]
     d = _json_lines(p.stdout)[0]
     assert d["transport"] == "rccl" and d["world"] == 2
+
+
+def test_dump_sample_is_fixed_and_bounded():
+    """--dump-outputs writes an array whole up to DUMP_MAX_ELEMS elements and a
+    seeded sample in index order beyond it: the same elements every run."""
+    import numpy as np
+    b = _bench_module()
+    small = np.arange(1000, dtype=np.float64)
+    assert b.dump_sample(small) is small
+    big = np.arange(b.DUMP_MAX_ELEMS + 12345, dtype=np.float64)
+    s1, s2 = b.dump_sample(big), b.dump_sample(big.copy())
+    assert s1.shape == (b.DUMP_MAX_ELEMS,) and s1.dtype == np.float64 and np.array_equal(s1, s2)
+    assert np.all(np.diff(s1) > 0)  # distinct elements, index order
+    assert 2 * 8 * b.DUMP_MAX_ELEMS + (1 << 20) <= 64 * 10**6  # w + alpha + the small arrays

@@ -13,7 +13,7 @@ for rep in $(seq 1 ${REPS:-2}); do
   for v in "$@"; do
     i=$((i+1))
     envs="${v%%--*}"; flags="${v#*--}"
-    env X=0 $envs timeout -k 10 300 python3 bench.py --steps $STEPS --warmup 3 --no-cpu-baseline --no-gap $flags \
+    env X=0 $envs timeout -k 10 300 python3 bench.py --full --steps $STEPS --warmup 3 --no-cpu-baseline --no-gap $flags \
       > $O/${TAG}_${i}_${rep}.json 2> $O/${TAG}_${i}_${rep}.err || exit $?
     python3 - "$O/${TAG}_${i}_${rep}.json" "$v" <<'PY'
 import json, sys

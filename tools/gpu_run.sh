@@ -3,7 +3,7 @@
 #   tools/gpu_run.sh STEP [STEP ...]      (TAG=name labels the outputs)
 #   tests            pytest -m gpu (TESTS="-k expr" or a file list narrows it)
 #   smoke            __graft_entry__.smoke()
-#   bench            the default bench line (BENCH_ARGS adds flags)
+#   bench            the bench line with every extra measurement (--full; BENCH_ARGS adds flags)
 #   prof             rocprofv3 --kernel-trace --stats of a short bench
 #   pmc              FETCH_SIZE / WRITE_SIZE passes (+ calibration) of the same bench
 #   lines            the C5 / C3 / C4 config lines
@@ -22,7 +22,7 @@ PROFRUN="python3 bench.py --steps 50 --warmup 20 --no-cpu-baseline --no-gap ${BE
 
 line() {  # name, args...
   local n=$1; shift
-  timeout -k 10 600 python3 bench.py "$@" > $O/line_${n}_$TAG.json 2> $O/line_${n}_$TAG.err || return $?
+  timeout -k 10 600 python3 bench.py --full "$@" > $O/line_${n}_$TAG.json 2> $O/line_${n}_$TAG.err || return $?
   python3 -c "import json;d=json.loads(open('$O/line_${n}_$TAG.json').readlines()[-1]);print('$n', round(d['ms_per_step'],3), '%.4g'%d['value'], d['plan']['solver'], d.get('time_to_gap_s'), d.get('rounds_to_gap'), d['kernel_ms'], 'frac', round(d['roofline']['frac'],3), round(d['roofline_eval']['frac'],3))"
 }
 
@@ -37,7 +37,7 @@ for step in "$@"; do
       timeout -k 10 300 python3 -c "import __graft_entry__ as g; g.smoke()" > $O/smoke_$TAG.log 2>&1 || exit $?
       tail -1 $O/smoke_$TAG.log ;;
     bench)
-      timeout -k 10 600 python3 bench.py ${BENCH_ARGS} > $O/bench_$TAG.json 2> $O/bench_$TAG.err || exit $?
+      timeout -k 10 600 python3 bench.py --full ${BENCH_ARGS} > $O/bench_$TAG.json 2> $O/bench_$TAG.err || exit $?
       tail -1 $O/bench_$TAG.json ;;
     prof)
       timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/rocprof_$TAG -o run --output-format csv -- $PROFRUN \
@@ -82,7 +82,7 @@ for step in "$@"; do
       done ;;
     evalab)  # eval kernel variants (COCOA_EVAL_VARIANT) on the C2 bench
       for v in ${EVAL_VARIANTS:-0 1 2}; do
-        COCOA_EVAL_VARIANT=$v timeout -k 10 300 python3 bench.py --steps 10 --warmup 2 --no-cpu-baseline --no-gap ${BENCH_ARGS} \
+        COCOA_EVAL_VARIANT=$v timeout -k 10 300 python3 bench.py --full --steps 10 --warmup 2 --no-cpu-baseline --no-gap ${BENCH_ARGS} \
           > $O/evalab_${v}_$TAG.json 2> $O/evalab_${v}_$TAG.err || exit $?
         python3 -c "import json;d=json.loads(open('$O/evalab_${v}_$TAG.json').readlines()[-1]);print('eval variant $v', round(d['roofline_eval']['avg_launch_ms'],4), 'ms', round(d['roofline_eval']['frac'],3), 'step', round(d['ms_per_step'],3), 'gap[-1]', repr(d['gap_trajectory_timed'][-1]))"
       done ;;
@@ -109,7 +109,7 @@ for step in "$@"; do
         lib=cocoa_amd/libcocoa_hip.so; [ "$name" = base ] || lib=build/v_$name/libcocoa_hip.so
         [ "$name" = diag ] && lib=build/diag/libcocoa_hip.so
         v=${v//=/_}
-        env $envset COCOA_LIB=$lib timeout -k 10 300 python3 bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-gap ${BENCH_ARGS} \
+        env $envset COCOA_LIB=$lib timeout -k 10 300 python3 bench.py --full --steps 20 --warmup 3 --no-cpu-baseline --no-gap ${BENCH_ARGS} \
           > $O/ab_${v}_$TAG.json 2> $O/ab_${v}_$TAG.err || exit $?
         python3 -c "import json;d=json.loads(open('$O/ab_${v}_$TAG.json').readlines()[-1]);k=d['kernel_ms'];print('$v', 'step', round(d['ms_per_step'],4), 'solver', round(k['solver'],4), 'gram', round(k.get('gram',0),4), 'eval', round(d['roofline_eval']['avg_launch_ms'],4), 'gap[-1]', repr(d['gap_trajectory_timed'][-1]))"
       done ;;
