@@ -2741,8 +2741,10 @@ void cocoa_ctx::eval_quiesce() {
         inl_ranks = false;
     }
     if (!eval_pending) return;
-    eval_fire(this);
-    HIPCHK(hipEventSynchronize(e_done));
+    // (never enqueued -- no round since cocoa_eval_async: nothing reads the data
+    // being replaced, and enqueueing it now would need an initialised context,
+    // which cocoa_set_solver before this cocoa_init has just revoked)
+    if (eval_fired) HIPCHK(hipEventSynchronize(e_done));
     eval_pending = false;
 }
 
@@ -3431,12 +3433,14 @@ static void group_set_train(cocoa_ctx* g, bool dense, int32_t K, const int64_t* 
     g->has_test = false;
     g->te.n = 0;
     g->inited = false;
+    g->inl_pending = g->inl_ranks = false;  // (the result it held was of the rows just replaced)
 }
 
 static void group_set_test(cocoa_ctx* g, bool dense, const int64_t* row_ptr, const int32_t* col, const double* val,
                            const double* y, int64_t n_rows) {
     const int32_t N = (int32_t)g->subs.size();
     require(g->d > 0, COCOA_E_STATE, "cocoa_set_test: call cocoa_set_train first");
+    g->inl_pending = g->inl_ranks = false;  // a pending evaluation is dropped (set_test_impl's eval_quiesce)
     require(y && n_rows >= 0 && (dense || row_ptr), COCOA_E_ARG, "cocoa_set_test: bad argument");
     if (!dense) require(row_ptr[0] == 0, COCOA_E_ARG, "row_ptr[0] must be 0");
     g->g_t0.assign((size_t)N + 1, 0);
@@ -3474,6 +3478,7 @@ static void group_init(cocoa_ctx* g, const cocoa_params* params, const cocoa_deb
     g->method = method;
     g->scaling = g->subs[0]->scaling;
     g->alpha_oob = false;
+    g->inl_pending = g->inl_ranks = false;  // an uncollected cocoa_eval_begin is dropped, as on one device
     const size_t N = g->subs.size();
     if (!g->strict && N > 1)
         for (size_t r = 0; r < N; ++r) {
