@@ -144,6 +144,15 @@ SIGNATURES = {
     "cocoa_comm_destroy": (_int, [_vp]),
     "cocoa_comm_allreduce": (_int, [_vp, _pf64, _i64]),
     "cocoa_comm_ordered_sum": (_int, [_vp, _pf64, _i64]),
+    "cocoa_score": (_int, [_vp, _pf64, _pi64, _pi32, _pf64, _i64, _i32, _pf64]),
+    "cocoa_score_dense": (_int, [_vp, _pf64, _pf64, _i64, _i32, _pf64]),
+    "cocoa_score_device": (_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i32, _vp]),
+    "cocoa_score_dense_device": (_int, [_vp, _vp, _vp, _i64, _i32, _vp]),
+    "cocoa_score_set_chunk": (_int, [_vp, _i64]),
+    "cocoa_score_errors": (_int, [_pf64, _pf64, _i64, _pi64]),
+    "cocoa_model_save": (_int, [ctypes.c_char_p, _pf64, _i32, ctypes.c_char_p, _f64, _i32]),
+    "cocoa_model_load": (_int, [ctypes.c_char_p, ctypes.POINTER(_pf64), _pi32]),
+    "cocoa_model_free": (None, [_pf64]),
 }
 
 TRANSPORTS = {"rccl": 0, "host": 1, "local": 2}

@@ -2,7 +2,9 @@
 // (hingeDriver.scala:9-115): same --key=value flags and defaults, same stdout
 // lines, with the solvers running on the MI355X through libcocoa_hip.so's C ABI
 // instead of Spark executors.  Extra flags: --device=<ordinal>,
-// --strict=<bool> (bit-exact mode, default false).
+// --strict=<bool> (bit-exact mode, default false), --modelDir=<dir> (write each
+// method's final w to <dir>/<slug>.model, cocoa_model_save; nothing extra on
+// stdout).
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -80,6 +82,14 @@ void summary(const char* alg, cocoa_ctx* ctx, bool primal_dual, bool test) {
     std::fflush(stdout);
 }
 
+// --modelDir: the method's final w as a COCOA-MODEL 1 file for cocoa_predict
+void save_model(const std::string& dir, const char* slug, cocoa_ctx* ctx, int d, double lambda, int rounds) {
+    if (dir.empty()) return;
+    std::vector<double> w((size_t)d);
+    check(cocoa_get_w(ctx, w.data()), ctx);
+    check(cocoa_model_save((dir + "/" + slug + ".model").c_str(), w.data(), d, slug, lambda, rounds));
+}
+
 }  // namespace
 
 int main(int argc, char** argv) {
@@ -121,6 +131,7 @@ int main(int argc, char** argv) {
         const int seed = to_int(get("seed", "0"));
         const int device = to_int(get("device", "0"));
         const bool strict = to_bool(get("strict", "false"));
+        const std::string modelDir = get("modelDir", "");
 
         // hingeDriver.scala:41-48 (including its label quirk on line 47)
         std::printf("master:       %s\ntrainFile:    %s\n", master.c_str(), trainFile.c_str());
@@ -157,13 +168,14 @@ int main(int argc, char** argv) {
             const char* banner;
             const char* summary;
             bool pd;
+            const char* slug;
         };
-        std::vector<M> ms = {{COCOA_METHOD_COCOA_PLUS, "CoCoA+", "CoCoA+", true},
-                             {COCOA_METHOD_COCOA, "CoCoA", "CoCoA", true}};
+        std::vector<M> ms = {{COCOA_METHOD_COCOA_PLUS, "CoCoA+", "CoCoA+", true, "cocoa_plus"},
+                             {COCOA_METHOD_COCOA, "CoCoA", "CoCoA", true, "cocoa"}};
         if (!justCoCoA) {
-            ms.push_back({COCOA_METHOD_MBCD, "Mini-batch CD", "Mini-batch CD", true});
-            ms.push_back({COCOA_METHOD_MBSGD, "SGD (with local updates = false)", "Mini-batch SGD", false});
-            ms.push_back({COCOA_METHOD_LOCALSGD, "SGD (with local updates = true)", "Local SGD", false});
+            ms.push_back({COCOA_METHOD_MBCD, "Mini-batch CD", "Mini-batch CD", true, "mbcd"});
+            ms.push_back({COCOA_METHOD_MBSGD, "SGD (with local updates = false)", "Mini-batch SGD", false, "mbsgd"});
+            ms.push_back({COCOA_METHOD_LOCALSGD, "SGD (with local updates = true)", "Local SGD", false, "localsgd"});
         }
         for (const M& m : ms) {
             std::printf("\nRunning %s on %d data examples, distributed over %d workers\n", m.banner, n, K);
@@ -171,6 +183,7 @@ int main(int argc, char** argv) {
             Printer pr{has_test, m.pd};
             check(cocoa_run(ctx, &P, &D, m.method, nullptr, on_round, &pr), ctx);
             summary(m.summary, ctx, m.pd, has_test);
+            save_model(modelDir, m.slug, ctx, numFeatures, lambda, numRounds);
         }
         if (!justCoCoA) {
             // DistGD (hingeDriver.scala:107-109) is outside this engine's scope; the

@@ -127,6 +127,10 @@ struct cocoa_comm {
     cocoa::Comm* c = nullptr;
 };
 
+// buffers of the scoring entry points (score_impl.h), made on first use
+struct ScoreState;
+static void score_state_free(cocoa_ctx* c);
+
 struct cocoa_ctx {
     int device = 0;
     bool strict = false;
@@ -157,6 +161,7 @@ struct cocoa_ctx {
     bool own_stream = false;
     std::string err;
     std::string ckpt_dir;  // cocoa_set_checkpoint_dir: periodic (t, w, alpha) saves in cocoa_run
+    ScoreState* score = nullptr;  // cocoa_score*: staging slots, original-order w (score_impl.h)
     // Double-buffered deltaW slices (large K_loc * d, e.g. C4): round t works in
     // set t & 1; the set round t folded is re-zeroed by a memset on zstream
     // that starts with round t+1 (after round t's eval, so the bandwidth-bound
@@ -431,6 +436,7 @@ struct cocoa_ctx {
         }
         if (!subs.empty()) (void)hipSetDevice(device);
         if (stream) (void)hipStreamSynchronize(stream);
+        score_state_free(this);
         if (gstream) {
             (void)hipStreamSynchronize(gstream);
             (void)hipStreamDestroy(gstream);
@@ -3839,3 +3845,6 @@ extern "C" int cocoa_gram_fallback_count(cocoa_ctx* ctx, int32_t* out) {
     }
     CAPI_END(ctx)
 }
+
+// ---------------------------------------------------------------- scoring --
+#include "score_impl.h"

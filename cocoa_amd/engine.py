@@ -49,6 +49,27 @@ class Comm:
             pass
 
 
+def save_model(path, w, method="unknown", lam=0.0, rounds=0):
+    """Write w (original feature order) as a text COCOA-MODEL 1 file
+    (cocoa_model_save): a header, then one java.lang.Double.toString per weight."""
+    w = np.ascontiguousarray(w, np.float64)
+    if w.ndim != 1:
+        raise C.IllegalArgumentError(C.E_ARG, "save_model: w must be 1-D")
+    C.check(C.lib().cocoa_model_save(os.fsencode(path), C.f64p(w), len(w), str(method).encode(), float(lam),
+                                     int(rounds)))
+
+
+def load_model(path):
+    """The weights of a COCOA-MODEL 1 file (cocoa_model_load), bitwise what was saved."""
+    wp = ctypes.POINTER(ctypes.c_double)()
+    d = ctypes.c_int32(0)
+    C.check(C.lib().cocoa_model_load(os.fsencode(path), ctypes.byref(wp), ctypes.byref(d)))
+    try:
+        return np.ctypeslib.as_array(wp, (d.value,)).copy()
+    finally:
+        C.lib().cocoa_model_free(wp)
+
+
 def _dense_rows(data, chunk=1 << 14):
     """Rows that store every feature 0..d-1 in index order (epsilon-shaped, C3):
     the value array is then the row-major matrix itself."""
@@ -82,6 +103,7 @@ class Engine:
                                          ctypes.byref(h)))
         self.h = h
         self.strict = strict
+        self._stream = 0 if devices is not None else int(stream or 0)
         self.d = 0
         self.n_rows = 0
         self._keep = []
@@ -284,6 +306,117 @@ class Engine:
         out = np.zeros(count, np.int32)
         C.check(C.lib().cocoa_samples(self.h, part, seed_plus_t, count, C.i32p(out)), self.h)
         return out
+
+    # -- scoring -------------------------------------------------------------
+    def score_set_chunk(self, max_entries=0):
+        """Entries per host chunk of decision_function on host rows (0: the default)."""
+        C.check(C.lib().cocoa_score_set_chunk(self.h, int(max_entries)), self.h)
+
+    def decision_function(self, X, w=None):
+        """f = X w (cocoa_score*): one decision value per row of X.
+
+        X: a LabeledData, a 2-D numpy array (host rows; returns numpy
+        float64[n]), or a torch CUDA tensor, dense 2-D or sparse_csr (rows
+        already on the GPU; returns a torch tensor on the same device).
+        w: the model in original feature order (numpy for host rows, a torch
+        tensor on X's device or numpy for torch rows); None = the engine's
+        current w.  torch rows: torch's stream is synchronised before the call
+        and the engine after it, unless the engine was created on torch's
+        current stream."""
+        from .data import LabeledData
+        if isinstance(X, LabeledData):
+            X = X.contiguous()
+            wp = self._host_w(w, X.num_features)
+            out = np.zeros(X.n, np.float64)
+            C.check(C.lib().cocoa_score(self.h, wp[1], C.i64p(X.row_ptr), C.i32p(X.col), C.f64p(X.val), X.n,
+                                        X.num_features, C.f64p(out)), self.h)
+            return out
+        if isinstance(X, np.ndarray):
+            if X.ndim != 2:
+                raise C.IllegalArgumentError(C.E_ARG, "decision_function: a numpy X must be 2-D [n, d]")
+            X = np.ascontiguousarray(X, np.float64)
+            wp = self._host_w(w, X.shape[1])
+            out = np.zeros(X.shape[0], np.float64)
+            C.check(C.lib().cocoa_score_dense(self.h, wp[1], C.f64p(X), X.shape[0], X.shape[1], C.f64p(out)), self.h)
+            return out
+        return self._decision_function_torch(X, w)
+
+    @staticmethod
+    def _host_w(w, d):
+        if w is None:
+            return None, None
+        w = np.ascontiguousarray(w, np.float64)
+        if w.shape != (d,):
+            raise C.IllegalArgumentError(C.E_ARG, "decision_function: w must have shape (%d,)" % d)
+        return w, C.f64p(w)
+
+    def _decision_function_torch(self, X, w):
+        import torch
+        if not isinstance(X, torch.Tensor) or not X.is_cuda or X.dim() != 2:
+            raise C.IllegalArgumentError(C.E_ARG, "decision_function: X must be a LabeledData, a 2-D numpy array "
+                                                  "or a 2-D torch CUDA tensor (dense or sparse_csr)")
+        n, d = int(X.shape[0]), int(X.shape[1])
+        keep = []
+        wptr = None
+        if w is not None:
+            wt = w if isinstance(w, torch.Tensor) else torch.as_tensor(np.ascontiguousarray(w, np.float64))
+            wt = wt.to(device=X.device, dtype=torch.float64).contiguous()
+            if tuple(wt.shape) != (d,):
+                raise C.IllegalArgumentError(C.E_ARG, "decision_function: w must have shape (%d,)" % d)
+            keep.append(wt)
+            wptr = ctypes.c_void_p(wt.data_ptr())
+        out = torch.empty(n, dtype=torch.float64, device=X.device)
+        same_stream = bool(self._stream) and self._stream == torch.cuda.current_stream(X.device).cuda_stream
+        if X.layout == torch.sparse_csr:
+            crow, col, val = X.crow_indices(), X.col_indices(), X.values()
+            if crow.dtype != torch.int64:
+                crow = crow.to(torch.int64)
+            if col.dtype != torch.int32:
+                col = col.to(torch.int32)
+            if val.dtype != torch.float64:
+                val = val.to(torch.float64)
+            keep += [crow, col, val]
+            nnz = int(val.shape[0])
+            if not same_stream:
+                torch.cuda.synchronize(X.device)
+            C.check(C.lib().cocoa_score_device(self.h, wptr, ctypes.c_void_p(crow.data_ptr()),
+                                               ctypes.c_void_p(col.data_ptr() if nnz else 0),
+                                               ctypes.c_void_p(val.data_ptr() if nnz else 0), n, nnz, d,
+                                               ctypes.c_void_p(out.data_ptr() if n else 0)), self.h)
+        elif X.layout == torch.strided:
+            Xc = X.to(torch.float64).contiguous()
+            keep.append(Xc)
+            if not same_stream:
+                torch.cuda.synchronize(X.device)
+            C.check(C.lib().cocoa_score_dense_device(self.h, wptr, ctypes.c_void_p(Xc.data_ptr() if n else 0), n, d,
+                                                     ctypes.c_void_p(out.data_ptr() if n else 0)), self.h)
+        else:
+            raise C.IllegalArgumentError(C.E_ARG, "decision_function: torch X must be dense or sparse_csr")
+        if not same_stream:
+            self.sync()
+        del keep
+        return out
+
+    def predict(self, X, w=None):
+        """+1.0 where the decision value is > 0, else -1.0 (same container kind as decision_function)."""
+        f = self.decision_function(X, w)
+        if isinstance(f, np.ndarray):
+            return np.where(f > 0, 1.0, -1.0)
+        import torch
+        return torch.where(f > 0, torch.ones_like(f), -torch.ones_like(f))
+
+    @staticmethod
+    def score_errors(f, y):
+        """Rows with !(f * y > 0) (cocoa_score_errors; OptUtils.computeClassificationError's rule)."""
+        if not isinstance(f, np.ndarray) and hasattr(f, "cpu"):
+            f = f.cpu().numpy()
+        f = np.ascontiguousarray(f, np.float64)
+        y = np.ascontiguousarray(y, np.float64)
+        if f.shape != y.shape or f.ndim != 1:
+            raise C.IllegalArgumentError(C.E_ARG, "score_errors: f and y must be 1-D of equal length")
+        n = ctypes.c_int64(0)
+        C.check(C.lib().cocoa_score_errors(C.f64p(f), C.f64p(y), len(f), ctypes.byref(n)))
+        return n.value
 
     # -- profiling -----------------------------------------------------------
     def stats_enable(self, on=True):

@@ -267,7 +267,76 @@ int cocoa_get_alpha(cocoa_ctx *ctx, double *alpha_out);   /* this rank's n_rows 
 int cocoa_set_w(cocoa_ctx *ctx, const double *w_in);
 int cocoa_set_alpha(cocoa_ctx *ctx, const double *alpha_in);
 
-/* (t, w, alpha) checkpoint of this rank.  The reference checkpoints its alpha
+/* ---- scoring (decision values of unseen rows) ------------------------------ */
+/* f_r = sum over row r's stored entries of val * w[col]: the x.w that
+ * computeClassificationError tests (OptUtils.scala:95-98), per row.  Columns
+ * and w are in original feature order.  Strict contexts sum every row in stored
+ * order, product then add (bitwise the oracle's dot); fast contexts reduce in
+ * tiles (within 1e-9 of sum |val * w[col]|, the same bytes on every call for
+ * the same input and chunk size).  The presence of these symbols is the
+ * feature test (COCOA_CAPI_VERSION is unchanged).
+ *
+ * Scoring keeps its own buffers and only enqueues behind the work queued on the
+ * context's stream: it may be called between rounds and while an evaluation is
+ * pending (cocoa_eval_begin / cocoa_eval_async), and changes neither their
+ * results nor the next round.
+ *
+ * f = X w for caller rows in host memory.  w: host double[num_features] in
+ * original feature order, or NULL = the context's current w (COCOA_E_STATE
+ * before cocoa_init).  With w given the context needs no training set; with a
+ * training set num_features must equal its d (COCOA_E_ARG).  row_ptr must start
+ * at 0 and be monotone (COCOA_E_ARG); a column outside [0, num_features) is
+ * COCOA_E_RANGE, as in the loader.  The rows travel in chunks of at most
+ * max_entries entries (and rows) cut at row boundaries, a longer row being a
+ * chunk of its own, through two pinned staging buffers (chunk i+1 uploads while
+ * chunk i computes), so device memory stays bounded by two chunks.  On a
+ * multi-device context device r scores the contiguous row block
+ * [n r / N, n (r+1) / N).  Returns with out filled. */
+int cocoa_score(cocoa_ctx *ctx, const double *w, const int64_t *row_ptr, const int32_t *col, const double *val,
+                int64_t n_rows, int32_t num_features, double *out);
+/* Row-major X[n_rows][num_features], every feature stored in index order. */
+int cocoa_score_dense(cocoa_ctx *ctx, const double *w, const double *X, int64_t n_rows, int32_t num_features,
+                      double *out);
+/* The same for rows already on the context's device: row_ptr_dev int64[n_rows+1]
+ * (row_ptr[0] = 0, row_ptr[n_rows] = nnz), col_dev int32[nnz], val_dev
+ * double[nnz], w_dev double[num_features] (NULL = the context's w), out_dev
+ * double[n_rows], each naturally aligned (views into larger allocations are
+ * fine).  Enqueued on the context's stream; returns without waiting for the
+ * result (cocoa_sync, or stream order, makes out_dev visible).  The host never
+ * reads the device arrays, so nothing is validated: a column outside
+ * [0, num_features) or a row_ptr that does not describe nnz entries is the
+ * caller's error (precondition).  The buffers must stay alive until the work
+ * has run.  COCOA_E_STATE on a multi-device context. */
+int cocoa_score_device(cocoa_ctx *ctx, const void *w_dev, const void *row_ptr_dev, const void *col_dev,
+                       const void *val_dev, int64_t n_rows, int64_t nnz, int32_t num_features, void *out_dev);
+int cocoa_score_dense_device(cocoa_ctx *ctx, const void *w_dev, const void *X_dev, int64_t n_rows,
+                             int32_t num_features, void *out_dev);
+/* Entries per host chunk of cocoa_score / cocoa_score_dense (0 = the default,
+ * 4 Mi entries). */
+int cocoa_score_set_chunk(cocoa_ctx *ctx, int64_t max_entries);
+/* computeClassificationError's rule on scores (OptUtils.scala:95-98): the
+ * number of rows with !(f * y > 0) -- a zero or NaN score is an error for
+ * either label.  Host only. */
+int cocoa_score_errors(const double *f, const double *y, int64_t n_rows, int64_t *err_count);
+
+/* Model file, host only (no context, no device).  Text:
+ *   COCOA-MODEL 1
+ *   numFeatures <d>
+ *   method <name>
+ *   lambda <Double.toString>
+ *   rounds <T>
+ *   <d lines, Double.toString(w_j), original feature order>
+ * Doubles are written as java.lang.Double.toString prints them and read back
+ * correctly rounded, so a save / load round trip is bitwise (-0.0, subnormals,
+ * NaN and +-Infinity included).  Load: COCOA_E_IO for a file that cannot be
+ * read, COCOA_E_PARSE for a wrong magic, header, line count or number.  *w_out
+ * is allocated by the library; free it with cocoa_model_free. */
+int cocoa_model_save(const char *path, const double *w, int32_t num_features, const char *method, double lambda,
+                     int32_t rounds);
+int cocoa_model_load(const char *path, double **w_out, int32_t *num_features);
+void cocoa_model_free(double *w);
+
+/* (t, w, alpha) checkpoint of this rank. The reference checkpoints its alpha
  * RDD every chkptIter rounds only to truncate Spark lineage
  * (CoCoA.scala:58-62); here the round state goes to a file so that a long run
  * (config C4) can stop and resume.  Format "COCOACK1", little-endian: a
